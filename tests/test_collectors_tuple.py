@@ -7,6 +7,7 @@ releases per-tuple total order; kslack_collector.hpp:52 buffers/drops per
 tuple) and assert exact order / accounting at the sink.
 """
 import random
+import threading
 
 import numpy as np
 import pytest
@@ -159,16 +160,36 @@ def test_kslack_drops_are_per_tuple():
     """One ancient row inside an otherwise-ordered batch: only THAT row is
     dropped (round 1 dropped whole batches)."""
     n, batch = 5000, 100
+    late_at = 4000
     ts = list(range(n))
-    ts[4000] = 7  # one ancient timestamp mid-stream
+    ts[late_at] = 7  # one ancient timestamp mid-stream
     seen = []
+    caught_up = threading.Event()
 
     def sink(cols):
         seen.extend(cols['ts'].tolist())
+        if len(seen) >= late_at:
+            caught_up.set()
+
+    # "Ancient" means behind what the collector has already released, so the
+    # source holds the batch carrying the late row until the sink has taken
+    # every earlier row; a source that outruns the sink thread would
+    # otherwise park the whole stream in the slack heap, where ts=7 is
+    # simply in order.
+    inner = _striped_source(ts, batch)
+    emitted = dict(rows=0)
+
+    def paced_source(replica, par):
+        if emitted['rows'] == late_at:
+            assert caught_up.wait(60), "sink never received the earlier rows"
+        out = inner(replica, par)
+        if out is not None:
+            emitted['rows'] += len(out['ts'])
+        return out
 
     g = wf.PipeGraph("ks1", wf.ExecutionMode.PROBABILISTIC,
                      wf.TimePolicy.EVENT_TIME)
-    mp = g.add_source(wf.Source_Builder(_striped_source(ts, batch))
+    mp = g.add_source(wf.Source_Builder(paced_source)
                       .withParallelism(1).withOutputSchema([0])
                       .withOutputBatchSize(batch).build())
     snk = wf.Sink_Builder(sink).withParallelism(1).build()
