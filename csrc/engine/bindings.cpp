@@ -643,15 +643,16 @@ PYBIND11_MODULE(_core, m) {
           });
     m.def("debug_ffat_stage_times",
           [](int64_t n, int64_t n_keys, int64_t win, int64_t slide, int iters,
-             int vik) {
+             int vik, const std::string& fold_variant) {
               py::dict d;
-              for (auto& [k, v] :
-                   debug_ffat_stage_times(n, n_keys, win, slide, iters, vik))
+              for (auto& [k, v] : debug_ffat_stage_times(n, n_keys, win, slide,
+                                                         iters, vik, fold_variant))
                   d[py::str(k)] = v;
               return d;
           },
           py::arg("n"), py::arg("n_keys"), py::arg("win") = 1000,
-          py::arg("slide") = 100, py::arg("iters") = 20, py::arg("vik") = 0);
+          py::arg("slide") = 100, py::arg("iters") = 20, py::arg("vik") = 0,
+          py::arg("fold_variant") = "");
     m.def("debug_tb_stage_times",
           [](int64_t n, int64_t n_keys, int iters, int mono) {
               std::map<std::string, double> m2;

@@ -505,7 +505,8 @@ std::pair<std::vector<uint32_t>, std::vector<uint32_t>> debug_sort_pairs_host(
 std::vector<uint32_t> debug_key_slots_host(const uint64_t* keys, int64_t n,
                                            int64_t max_keys);
 std::vector<std::pair<std::string, double>> debug_ffat_stage_times(
-    int64_t n, int64_t n_keys, int64_t win, int64_t slide, int iters, int vik);
+    int64_t n, int64_t n_keys, int64_t win, int64_t slide, int iters, int vik,
+    const std::string& fold_variant = "");
 std::vector<std::pair<std::string, double>> debug_gram_stage_times(
     int64_t n, int64_t n_keys, int64_t win, int iters);
 std::vector<std::pair<std::string, double>> debug_tb_stage_times(

@@ -813,18 +813,32 @@ struct GpuFfatLogic : GpuLogicBase {
     Engine* eng_ = nullptr;        // central dropped-tuple accounting
     int64_t batches = 0;
     bool use_pane2 = false;
+    // which wave-per-segment fold wfa_ffat_cb_fold launches at pane_len >=
+    // 32: the LDS-tiled kernel unless WFA_CB_FOLD=wave.  Read per operator
+    // at construction so one process can run both.
+    int cb_fold_variant = WFA_CB_FOLD_TILE;
+    static int cb_fold_from_env() {
+        const char* e = getenv("WFA_CB_FOLD");
+        return (e && !strcmp(e, "wave")) ? WFA_CB_FOLD_WAVE : WFA_CB_FOLD_TILE;
+    }
     // A/B on MI355X (8M-tuple batches): the two-stage fold wins when
     // segments are few (1024 keys: 16.9 vs 13.9 B t/s — the wave fold is
     // occupancy-bound at one wave per key) and loses slightly when the
-    // chip is already full (8192 keys: 18.6 vs 19.4).  Auto-select by key
-    // count; WFA_PANE2=0/1 forces either path.
+    // chip is already full (8192 keys: 18.6 vs 19.4).  That A/B was against
+    // the WAVE fold, and auto-selection by key count still applies to it.
+    // The tiled fold beats the two-stage fold at every key count measured
+    // (16M batches, step ms pane2 vs tiled: 16 keys 14.6/6.2, 64 3.89/1.83,
+    // 256 1.49/0.90, 1024 0.80/0.59, 2048 0.81/0.55 —
+    // profiles/ffat_stage_breakdown_r03.md), so with it auto means off.
+    // WFA_PANE2=0/1 forces either path.
     bool pane2_enabled() const {
         static int v = -1;
         if (v < 0) {
             const char* e = getenv("WFA_PANE2");
             v = e ? ((e[0] == '1') ? 1 : 0) : 2;  // 2 = auto
         }
-        if (v == 2) return max_keys <= 4096;
+        if (v == 2)
+            return cb_fold_variant == WFA_CB_FOLD_WAVE && max_keys <= 4096;
         return v == 1;
     }
 
@@ -847,6 +861,7 @@ struct GpuFfatLogic : GpuLogicBase {
         // the TB path); a requested tree layout silently falls back — same
         // results, different CB-only perf trade (round 1 threw here)
         if (tb && use_tree) use_tree = false;
+        cb_fold_variant = cb_fold_from_env();
     }
     void init_device() override {
         ks.alloc(device, out_cap, max_keys, stream);
@@ -991,7 +1006,8 @@ struct GpuFfatLogic : GpuLogicBase {
                              ks.v_as_f32, ks.v_dt, ks.idx_sorted, db->ts, pane_len, P, S,
                              comb, ring_log2, st_count, st_fill, st_acc,
                              ring_or_tree, st_head, st_wsum, ks.slot_to_key, nf,
-                             ob->key, (float*)ob->cols[0], ob->ts, ob->capacity);
+                             ob->key, (float*)ob->cols[0], ob->ts, ob->capacity,
+                             cb_fold_variant);
         HIPCHK(hipMemcpyAsync(ob->lazy_count, d_on, 8, hipMemcpyDeviceToHost, stream));
     }
 
@@ -1899,7 +1915,15 @@ std::vector<std::pair<std::string, double>> debug_a2a_stage_times(
 // for rocprofv3 kernel stats on this pool (profiling runs hang boxes);
 // drives perf work from real measurements, not guesses.
 std::vector<std::pair<std::string, double>> debug_ffat_stage_times(
-    int64_t n, int64_t n_keys, int64_t win, int64_t slide, int iters, int vik) {
+    int64_t n, int64_t n_keys, int64_t win, int64_t slide, int iters, int vik,
+    const std::string& fold_variant) {
+    int variant;
+    if (fold_variant.empty() || fold_variant == "tile") variant = WFA_CB_FOLD_TILE;
+    else if (fold_variant == "wave") variant = WFA_CB_FOLD_WAVE;
+    else if (fold_variant == "tile512") variant = WFA_CB_FOLD_TILE512;
+    else if (fold_variant == "tile2048") variant = WFA_CB_FOLD_TILE2048;
+    else throw std::runtime_error("debug_ffat_stage_times: unknown fold_variant '" +
+                                  fold_variant + "' (wave|tile|tile512|tile2048)");
     HIPCHK(hipSetDevice(0));
     hipStream_t s = nullptr;
     KeyedScratch ks;
@@ -1974,7 +1998,7 @@ std::vector<std::pair<std::string, double>> debug_ffat_stage_times(
                          vik ? (const void*)os_ : (const void*)d_val, vik ? 6 : 5,
                          oi, d_ts, pane, P, S, 0, ring_log2, st_count, st_fill,
                          st_acc, ring, st_head, st_wsum, ks.slot_to_key, nf, o_key,
-                         o_val, o_ts, fires_cap);
+                         o_val, o_ts, fires_cap, variant);
         HIPCHK(hipEventRecord(ev[5], s));
         HIPCHK(hipStreamSynchronize(s));
         if (it >= 0)
@@ -2176,7 +2200,8 @@ std::vector<uint32_t> debug_key_slots_host(const uint64_t*, int64_t, int64_t) {
 }
 std::vector<std::pair<std::string, double>> debug_ffat_stage_times(int64_t, int64_t,
                                                                    int64_t, int64_t,
-                                                                   int, int) {
+                                                                   int, int,
+                                                                   const std::string&) {
     throw std::runtime_error("built without HIP");
 }
 std::vector<std::pair<std::string, double>> debug_a2a_stage_times(int64_t, int64_t,

@@ -1473,6 +1473,241 @@ __global__ void k_ffat_cb_wave(const uint32_t* seg_start, const uint32_t* seg_sl
 #undef WCOMB
 }
 
+// ===== LDS-tiled pane-per-lane CB fold =====
+// Same wave-per-segment mapping as k_ffat_cb_wave, different work per tuple:
+//  * the wave streams its segment in tiles of T tuples through a per-wave
+//    LDS region; a tile's global loads are all issued before the first use
+//    (16 B per lane per load: the tile origin is rounded down to a 16 B
+//    boundary of the streamed array) and the NEXT tile's loads are in
+//    flight while the current one is folded;
+//  * lane p folds pane p of the tile sequentially from LDS — pane bounds are
+//    lane-index multiplications, there is no per-tuple division and no
+//    cross-lane reduction.  Every pane partial is therefore the plain
+//    in-order fold of its tuples (the first pane continues st_acc), so the
+//    bits depend on the data order alone, never on T, the grid or timing;
+//  * the slot's ring (R <= 64) lives in one register per lane (lane r = cell
+//    r), loaded once at segment start and written back once at the end; the
+//    serial window machine reads partials and ring cells with v_readlane and
+//    parks fired windows in lanes, which then write their rows (and chase
+//    ts_orig[idx_sorted[last]]) in parallel.  R > 64 keeps the ring in
+//    global memory exactly as k_ffat_cb_wave does.
+// State contract (st_fill/st_acc/st_head/st_wsum/st_count, ring cells
+// [head-P, head)) and fired-row positions are those of k_ffat_cb_wave.
+template <int COMB>
+__device__ __forceinline__ float tl_comb(float a, float b) {
+    return COMB == 1 ? fminf(a, b) : (COMB == 2 ? fmaxf(a, b) : a + b);
+}
+__device__ __forceinline__ float tl_readlane(float v, uint32_t l) {
+    return __int_as_float(__builtin_amdgcn_readlane(
+        __float_as_int(v), (int)__builtin_amdgcn_readfirstlane(l)));
+}
+// one wave exchanges data through its own LDS region: lanes run in
+// lockstep, so only the compiler has to be kept from reordering
+__device__ __forceinline__ void tl_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Register budget: the VIK tile (T/64 values per lane) fits 64 VGPRs, i.e. 8
+// waves per SIMD — all 8192 waves of the grid resident at once.  The gather
+// path also holds T/64 indices and is bounded to 6 waves so it does not spill.
+// (T = 2048 is an A/B size only: its 32 KB of LDS per block caps it lower.)
+template <int COMB, bool VIK, int T>
+__global__ __launch_bounds__(WFA_THREADS, T > 1024 ? (VIK ? 5 : 3) : (VIK ? 8 : 6))
+void k_ffat_cb_tile(
+    const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_slot,
+    const int64_t* __restrict__ d_nseg, int64_t n, const void* __restrict__ v_in,
+    int vdt, const uint32_t* __restrict__ idx_sorted,
+    const int64_t* __restrict__ ts_orig, int64_t pane_len, int64_t P_, int64_t S_,
+    int ring_log2, int64_t* st_count, uint32_t* st_fill, float* st_acc,
+    float* ring, uint32_t* st_head, float* st_wsum,
+    const uint64_t* __restrict__ slot_to_key,
+    const uint32_t* __restrict__ fire_base, uint64_t* __restrict__ out_key,
+    float* __restrict__ out_val, int64_t* __restrict__ out_ts, int64_t out_cap) {
+    constexpr int NV = T / 256;  // 16 B vectors per lane per tile
+    constexpr bool SUM = (COMB == 0 || COMB == 3);
+    __shared__ float4 tile_s[WFA_THREADS / 64][T / 4];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float* tl = (const float*)tile_s[wib];
+    const int64_t nseg = *d_nseg;
+    const uint32_t L = (uint32_t)pane_len, P = (uint32_t)P_, S = (uint32_t)S_;
+    const uint32_t R = 1u << ring_log2;
+    const uint32_t Rm = R - 1;
+    const bool onchip = R <= 64;
+    const float ident = (COMB == 1) ? INFINITY : (COMB == 2 ? -INFINITY : 0.f);
+    const int64_t wid = (int64_t)blockIdx.x * (WFA_THREADS / 64) + wib;
+    const int64_t nw = (int64_t)gridDim.x * (WFA_THREADS / 64);
+    // the array streamed 16 B at a time: sorted keys (VIK) or idx_sorted
+    const uint32_t* sp = VIK ? (const uint32_t*)v_in : idx_sorted;
+    const int64_t mis = (int64_t)(((uintptr_t)sp >> 2) & 3);
+    float vr[NV][4];
+
+    // issue every load of tile [a, a+T), valid tuples [p0, p1)
+    auto load_tile = [&](int64_t a, int64_t p0, int64_t p1) {
+        uint32_t u[NV][4];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int64_t q = a + 4 * (k * 64 + lane);
+            u[k][0] = u[k][1] = u[k][2] = u[k][3] = 0;
+            if (q + 3 >= p0 && q < p1) {
+                if (q >= 0 && q + 3 < n) {
+                    const uint4 t = *(const uint4*)(sp + q);
+                    u[k][0] = t.x; u[k][1] = t.y; u[k][2] = t.z; u[k][3] = t.w;
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (q + c >= p0 && q + c < p1) u[k][c] = sp[q + c];
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int64_t q = a + 4 * (k * 64 + lane);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (VIK) {
+                    vr[k][c] = __uint_as_float(u[k][c] << 16);
+                } else {
+                    vr[k][c] = (q + c >= p0 && q + c < p1)
+                                   ? wfa_val_at(v_in, vdt,
+                                                vdt == 7 ? q + c : (int64_t)u[k][c])
+                                   : ident;
+                }
+            }
+        }
+    };
+
+    for (int64_t j = wid; j < nseg; j += nw) {
+        const uint32_t slot = seg_slot[j];
+        const int64_t i0 = seg_start[j];
+        const int64_t e = (j + 1 < nseg) ? seg_start[j + 1] : n;
+        uint32_t fill = st_fill[slot];
+        float acc = st_acc[slot];
+        uint32_t head = st_head[slot];
+        float wsum = st_wsum[slot];
+        int64_t w = fire_base[j];
+        const uint64_t key = slot_to_key[slot];
+        float* rg = ring + (size_t)slot * R;
+        float rcell = (onchip && (uint32_t)lane < R) ? rg[lane] : ident;
+        const uint32_t head0 = head;
+        // fire phase (head - P) mod S, advanced incrementally per pane
+        uint32_t ph = head >= P ? (head - P) % S : 0;
+
+        int64_t pos = i0;
+        int64_t a = ((pos + mis) & ~(int64_t)3) - mis;
+        if (COMB != 3) load_tile(a, pos, min(e, a + T));
+        while (pos < e) {
+            const int64_t te = min(e, a + T);
+            const uint32_t lo = (uint32_t)(pos - a);
+            const uint32_t nt = (uint32_t)(te - pos);
+            if (COMB != 3) {
+#pragma unroll
+                for (int k = 0; k < NV; ++k)
+                    tile_s[wib][k * 64 + lane] =
+                        make_float4(vr[k][0], vr[k][1], vr[k][2], vr[k][3]);
+                tl_wave_sync();
+                if (te < e) load_tile(a + T, te, min(e, a + 2 * T));
+            }
+            const uint32_t np = (fill + nt + L - 1) / L;   // panes touched
+            const uint32_t ncomplete = (fill + nt) / L;    // panes finished
+            const float* src = tl + lo;
+            for (uint32_t pb = 0; pb < np; pb += 64) {
+                // lane p folds pane p: tile tuples [p*L - fill, (p+1)*L - fill)
+                const uint32_t p = pb + (uint32_t)lane;
+                float part = ident;
+                if (p < np) {
+                    const uint32_t s0 = p == 0 ? 0u : p * L - fill;
+                    const uint32_t s1 = (uint32_t)min(
+                        (uint64_t)nt, (uint64_t)(p + 1) * L - fill);
+                    if (p == 0) part = acc;
+                    if (COMB == 3) {
+                        part += (float)(s1 - s0);
+                    } else {
+#pragma unroll 4
+                        for (uint32_t t = s0; t < s1; ++t)
+                            part = tl_comb<COMB>(part, src[t]);
+                    }
+                }
+                // serial lane-uniform window machine over this round's panes
+                const uint32_t qend = min(ncomplete, pb + 64);
+                uint32_t nfire = 0;
+                float fval = 0.f;
+                uint32_t flast = 0;
+                for (uint32_t q = pb; q < qend; ++q) {
+                    const float pv = tl_readlane(part, q - pb);
+                    if (SUM) {
+                        wsum += pv;
+                        if (head >= P) {
+                            const uint32_t c = (head - P) & Rm;
+                            wsum -= onchip ? tl_readlane(rcell, c) : rg[c];
+                        }
+                    }
+                    if (onchip) {
+                        if ((uint32_t)lane == (head & Rm)) rcell = pv;
+                    } else if (lane == 0) {
+                        rg[head & Rm] = pv;
+                    }
+                    ++head;
+                    if (head == P) ph = 0;
+                    else if (head > P) ph = (ph + 1 == S) ? 0 : ph + 1;
+                    if (head >= P && ph == 0) {
+                        float res;
+                        if (SUM) {
+                            res = wsum;
+                        } else {
+                            float x = ident;
+                            if (onchip) {
+                                // lane r holds cell r: live if within P of head
+                                if ((uint32_t)lane < R &&
+                                    ((head - 1 - (uint32_t)lane) & Rm) < P)
+                                    x = rcell;
+                            } else {
+                                for (uint32_t z = lane; z < P; z += 64)
+                                    x = tl_comb<COMB>(
+                                        x, z == 0 ? pv : rg[(head - 1 - z) & Rm]);
+                            }
+                            for (int o = 32; o; o >>= 1)
+                                x = tl_comb<COMB>(x, __shfl_xor(x, o, 64));
+                            res = x;
+                        }
+                        if ((uint32_t)lane == nfire) {
+                            fval = res;
+                            flast = (q + 1) * L - fill - 1;  // completing tuple
+                        }
+                        ++nfire;
+                    }
+                }
+                // fired windows sit one per lane: write the rows in parallel
+                if ((uint32_t)lane < nfire && w + lane < out_cap) {
+                    out_key[w + lane] = key;
+                    out_val[w + lane] = fval;
+                    out_ts[w + lane] =
+                        ts_orig ? ts_orig[idx_sorted[pos + (int64_t)flast]] : 0;
+                }
+                w += nfire;
+                // the open tail pane (if any) is the new accumulator
+                if (np > ncomplete && ncomplete < pb + 64)
+                    acc = tl_readlane(part, ncomplete - pb);
+            }
+            if (np == ncomplete) acc = ident;
+            fill = fill + nt - ncomplete * L;
+            pos = te;
+            a += T;
+            if (COMB != 3) tl_wave_sync();
+        }
+        if (onchip && head != head0 && (uint32_t)lane < R) rg[lane] = rcell;
+        if (lane == 0) {
+            st_fill[slot] = fill;
+            st_acc[slot] = acc;
+            st_head[slot] = head;
+            st_wsum[slot] = wsum;
+            st_count[slot] += e - i0;
+        }
+    }
+}
+
 // ===== pane-wave CB fold =====
 // The serial per-key state machine above walks TUPLES; at pane_len >= 32
 // almost all of that walk is pane-partial accumulation, which is
@@ -1650,8 +1885,37 @@ extern "C" void wfa_ffat_cb_fold(wfa_stream_t s, const uint32_t* seg_start,
                                  uint32_t* st_head, float* st_wsum,
                                  const uint64_t* slot_to_key,
                                  const uint32_t* fire_base, uint64_t* out_key,
-                                 float* out_val, int64_t* out_ts, int64_t out_cap) {
-    if (pane_len >= 32)
+                                 float* out_val, int64_t* out_ts, int64_t out_cap,
+                                 int variant) {
+    if (pane_len >= 32 && variant != WFA_CB_FOLD_WAVE) {
+#define TL_LAUNCH(C, V, TT)                                                      \
+    hipLaunchKernelGGL((k_ffat_cb_tile<C, V, TT>), dim3(WFA_MAX_BLOCKS),         \
+                       dim3(WFA_THREADS), 0, (hipStream_t)s, seg_start,          \
+                       seg_slot, d_nseg, n, v_f32, vdt, idx_sorted, ts_orig,     \
+                       pane_len, P, S, ring_log2, st_count, st_fill, st_acc,     \
+                       ring, st_head, st_wsum, slot_to_key, fire_base, out_key,  \
+                       out_val, out_ts, out_cap)
+#define TL_VIK(C, TT)                                                            \
+    do {                                                                         \
+        if (vdt == 6) TL_LAUNCH(C, true, TT);                                    \
+        else TL_LAUNCH(C, false, TT);                                            \
+    } while (0)
+#define TL_COMB(TT)                                                              \
+    do {                                                                         \
+        switch (comb) {                                                          \
+            case 1: TL_VIK(1, TT); break;                                        \
+            case 2: TL_VIK(2, TT); break;                                        \
+            case 3: TL_VIK(3, TT); break;                                        \
+            default: TL_VIK(0, TT); break;                                       \
+        }                                                                        \
+    } while (0)
+        if (variant == WFA_CB_FOLD_TILE512) TL_COMB(512);
+        else if (variant == WFA_CB_FOLD_TILE2048) TL_COMB(2048);
+        else TL_COMB(1024);
+#undef TL_COMB
+#undef TL_VIK
+#undef TL_LAUNCH
+    } else if (pane_len >= 32)
         hipLaunchKernelGGL(k_ffat_cb_wave, dim3(WFA_MAX_BLOCKS), dim3(WFA_THREADS), 0,
                            (hipStream_t)s, seg_start, seg_slot, d_nseg, n, v_f32, vdt,
                            idx_sorted, ts_orig, pane_len, P, S, comb, ring_log2,

@@ -175,6 +175,18 @@ void wfa_ffat_cb_fold_pw(
 // Window: win = P panes of pane_len tuples, fires every S panes.
 // comb: 0 sum(invertible running total) 1 min 2 max  (min/max combine ring)
 // Output appended to out_* at atomic cursor d_out_n.
+// variant (pane_len >= 32 only): which wave-per-segment kernel folds.
+//   WAVE  k_ffat_cb_wave: 64-tuple chunks, masked wave reduce per pane
+//   TILE  k_ffat_cb_tile: LDS tiles of 1024 tuples, one pane per lane,
+//         ring in registers (the production choice)
+//   TILE512 / TILE2048: the same kernel at other tile sizes, for A/B
+//         timing through debug_ffat_stage_times
+enum {
+    WFA_CB_FOLD_WAVE = 0,
+    WFA_CB_FOLD_TILE = 1,
+    WFA_CB_FOLD_TILE512 = 2,
+    WFA_CB_FOLD_TILE2048 = 3,
+};
 void wfa_ffat_cb_fold(wfa_stream_t s, const uint32_t* seg_start,
                       const uint32_t* seg_slot, const int64_t* d_nseg, int64_t n,
                       const void* v_f32, int vdt, const uint32_t* idx_sorted,
@@ -185,7 +197,7 @@ void wfa_ffat_cb_fold(wfa_stream_t s, const uint32_t* seg_start,
                       float* ring, uint32_t* st_head, float* st_wsum,
                       const uint64_t* slot_to_key, const uint32_t* fire_base,
                       uint64_t* out_key, float* out_val, int64_t* out_ts,
-                      int64_t out_cap);
+                      int64_t out_cap, int variant);
 
 // fused two-stage CB fold: waves compute pane partials into LDS, wave 0
 // runs the window machine per chunk — one launch, no global pane traffic
