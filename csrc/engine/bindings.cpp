@@ -641,6 +641,36 @@ PYBIND11_MODULE(_core, m) {
               memcpy(vs.mutable_data(), r.second.data(), 4 * r.second.size());
               return py::make_tuple(ks, vs);
           });
+    m.def("debug_sort_pairs2",
+          [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> keys,
+             int bits, int base_shift, bool implicit_iota, bool prehist,
+             py::object vals2, const std::string& variant) {
+              const int64_t n = keys.shape(0);
+              py::array_t<uint32_t, py::array::c_style | py::array::forcecast> v2;
+              const uint32_t* v2p = nullptr;
+              if (!vals2.is_none()) {
+                  v2 = vals2.cast<py::array_t<uint32_t, py::array::c_style |
+                                                            py::array::forcecast>>();
+                  if (v2.ndim() != 1 || v2.shape(0) != n)
+                      throw std::runtime_error("debug_sort_pairs2: vals2 length");
+                  v2p = v2.data();
+              }
+              auto r = debug_sort_pairs2_host(keys.data(), n, bits, base_shift,
+                                              implicit_iota, prehist, v2p, variant);
+              py::array_t<uint32_t> ks((py::ssize_t)n), vs((py::ssize_t)n);
+              memcpy(ks.mutable_data(), r.keys.data(), 4 * n);
+              memcpy(vs.mutable_data(), r.idx.data(), 4 * n);
+              py::object w = py::none();
+              if (v2p) {
+                  py::array_t<uint32_t> ws((py::ssize_t)n);
+                  memcpy(ws.mutable_data(), r.vals2.data(), 4 * n);
+                  w = ws;
+              }
+              return py::make_tuple(ks, vs, w);
+          },
+          py::arg("keys"), py::arg("bits"), py::arg("base_shift") = 0,
+          py::arg("implicit_iota") = true, py::arg("prehist") = false,
+          py::arg("vals2") = py::none(), py::arg("variant") = "");
     m.def("debug_ffat_stage_times",
           [](int64_t n, int64_t n_keys, int64_t win, int64_t slide, int iters,
              int vik, const std::string& fold_variant) {

@@ -502,6 +502,13 @@ bool state_kv_erase(void* kv, void* cache, uint64_t key);
 // debug hooks (gpu_ops.cpp): device sort / hash-slot round trips
 std::pair<std::vector<uint32_t>, std::vector<uint32_t>> debug_sort_pairs_host(
     const uint32_t* keys, int64_t n, int bits);
+struct DebugSort2 {
+    std::vector<uint32_t> keys, idx, vals2;  // vals2 empty without a 2nd payload
+};
+DebugSort2 debug_sort_pairs2_host(const uint32_t* keys, int64_t n, int bits,
+                                  int base_shift, bool implicit_iota,
+                                  bool prehist, const uint32_t* vals2,
+                                  const std::string& variant);
 std::vector<uint32_t> debug_key_slots_host(const uint64_t* keys, int64_t n,
                                            int64_t max_keys);
 std::vector<std::pair<std::string, double>> debug_ffat_stage_times(

@@ -1702,6 +1702,79 @@ std::pair<std::vector<uint32_t>, std::vector<uint32_t>> debug_sort_pairs_host(
     return {std::move(hk), std::move(hv)};
 }
 
+// Sort round trip with every option of the 8-bit path exposed: base shift,
+// implicit/explicit index payload, second payload, pass-0 histogram from
+// the fused dense-key kernel, and the scatter variant ("" / "occ" / "lds").
+DebugSort2 debug_sort_pairs2_host(const uint32_t* keys, int64_t n, int bits,
+                                  int base_shift, bool implicit_iota,
+                                  bool prehist, const uint32_t* vals2,
+                                  const std::string& variant) {
+    int var;
+    if (variant.empty()) var = 0;
+    else if (variant == "occ") var = 1;
+    else if (variant == "lds") var = 2;
+    else throw std::runtime_error("debug_sort_pairs2: unknown variant '" + variant + "'");
+    if (n < 1 || bits < 1 || base_shift < 0 || base_shift + bits > 32)
+        throw std::runtime_error("debug_sort_pairs2: bad n / bits / base_shift");
+    if (prehist && base_shift != 0 && base_shift != 16)
+        throw std::runtime_error("debug_sort_pairs2: prehist needs base_shift 0 or 16");
+    HIPCHK(hipSetDevice(0));
+    auto& A = arena(0);
+    const size_t hb = 4 * wfa_sort_hist_u32(n);
+    uint32_t* d_k = (uint32_t*)A.get(4 * n);
+    uint32_t* d_v = (uint32_t*)A.get(4 * n);
+    uint32_t* d_kt = (uint32_t*)A.get(4 * n);
+    uint32_t* d_vt = (uint32_t*)A.get(4 * n);
+    uint32_t* d_w = vals2 ? (uint32_t*)A.get(4 * n) : nullptr;
+    uint32_t* d_wt = vals2 ? (uint32_t*)A.get(4 * n) : nullptr;
+    uint32_t* d_h = (uint32_t*)A.get(hb);
+    if (vals2) HIPCHK(hipMemcpy(d_w, vals2, 4 * n, hipMemcpyHostToDevice));
+    if (!implicit_iota) wfa_iota_u32(nullptr, d_v, n);
+    if (prehist) {
+        // production front end: the dense key kernel writes the (packed)
+        // slots and the sort's pass-0 histogram
+        std::vector<uint64_t> hk(n);
+        std::vector<uint16_t> hv(n);
+        for (int64_t i = 0; i < n; ++i) {
+            hk[i] = keys[i] >> base_shift;
+            hv[i] = (uint16_t)(keys[i] & 0xFFFF);
+        }
+        uint64_t* d_key = (uint64_t*)A.get(8 * n);
+        uint16_t* d_val = (uint16_t*)A.get(2 * n);
+        uint32_t* d_ns = (uint32_t*)A.get(64);
+        HIPCHK(hipMemcpy(d_key, hk.data(), 8 * n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_val, hv.data(), 2 * n, hipMemcpyHostToDevice));
+        wfa_fill_u32(nullptr, d_ns, 0, 2);
+        wfa_key_dense_h(nullptr, d_key, n, (int64_t)1 << bits, d_k, d_ns, d_ns + 1,
+                        base_shift ? d_val : nullptr, d_h, base_shift);
+        HIPCHK(hipStreamSynchronize(nullptr));
+        A.put(d_key, 8 * n); A.put(d_val, 2 * n); A.put(d_ns, 64);
+    } else {
+        HIPCHK(hipMemcpy(d_k, keys, 4 * n, hipMemcpyHostToDevice));
+    }
+    uint32_t *ok, *ov, *ow = nullptr;
+    if (prehist && var == 0)
+        wfa_sort_pairs2_ph(nullptr, d_k, d_v, d_kt, d_vt, d_w, d_wt, d_h, n, bits,
+                           &ok, &ov, &ow, implicit_iota ? 1 : 0, base_shift);
+    else
+        wfa_sort_pairs2_ex(nullptr, d_k, d_v, d_kt, d_vt, d_w, d_wt, d_h, n, bits,
+                           &ok, &ov, &ow, implicit_iota ? 1 : 0, base_shift,
+                           prehist ? 1 : 0, var, nullptr, nullptr);
+    DebugSort2 r;
+    r.keys.resize(n);
+    r.idx.resize(n);
+    HIPCHK(hipMemcpy(r.keys.data(), ok, 4 * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(r.idx.data(), ov, 4 * n, hipMemcpyDeviceToHost));
+    if (vals2) {
+        r.vals2.resize(n);
+        HIPCHK(hipMemcpy(r.vals2.data(), ow, 4 * n, hipMemcpyDeviceToHost));
+    }
+    A.put(d_k, 4 * n); A.put(d_v, 4 * n); A.put(d_kt, 4 * n); A.put(d_vt, 4 * n);
+    if (vals2) { A.put(d_w, 4 * n); A.put(d_wt, 4 * n); }
+    A.put(d_h, hb);
+    return r;
+}
+
 std::vector<uint32_t> debug_key_slots_host(const uint64_t* keys, int64_t n,
                                            int64_t max_keys) {
     HIPCHK(hipSetDevice(0));
@@ -2193,6 +2266,10 @@ Batch* gpu_clone_batch(Batch*) { throw std::runtime_error("built without HIP"); 
 std::string wfa_rccl_unique_id() { throw std::runtime_error("built without HIP"); }
 std::pair<std::vector<uint32_t>, std::vector<uint32_t>> debug_sort_pairs_host(
     const uint32_t*, int64_t, int) {
+    throw std::runtime_error("built without HIP");
+}
+DebugSort2 debug_sort_pairs2_host(const uint32_t*, int64_t, int, int, bool, bool,
+                                  const uint32_t*, const std::string&) {
     throw std::runtime_error("built without HIP");
 }
 std::vector<uint32_t> debug_key_slots_host(const uint64_t*, int64_t, int64_t) {

@@ -791,13 +791,221 @@ __global__ void k_rs8_scatter_lds(const uint32_t* keys, const uint32_t* vals,
     }
 }
 
+// Low-LDS variant of the staged scatter (same contract, same stable order,
+// same outputs as k_rs8_scatter_lds).  The LDS scatter's 48 KB per block
+// capped it at 3 blocks per CU; this one keeps the 4096-item tile and its
+// run lengths in 21.5 KB:
+//   - ONE 16 KB staging buffer, reused for the keys, then the payload, then
+//     (CARRY2) the second payload.  Each thread keeps its items' staged
+//     positions in registers, so a later round is an LDS write, a barrier,
+//     a read and a store.
+//   - no staged digit: the write loop takes it from the staged key and keeps
+//     it (packed above the 12-bit staged position) for the payload rounds.
+//   - the per-wave digit counters are overwritten in place with
+//     localBase + cross-wave prefix, and gbase - localBase is one array.
+//   - the two 256-entry scans (digit totals -> digit bases, block counts ->
+//     local bases) are wave shuffle scans with one cross-wave combine; the
+//     digit bases come straight from `dt`, so no k_rs8_dbase launch.
+//   - the payload is loaded only after the keys are staged (their registers
+//     are free by then); the loads fly while the keys are written out.
+__device__ __forceinline__ uint32_t rs8_wave_incl_scan(uint32_t v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        uint32_t t = (uint32_t)__shfl_up((int)v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// Register budget: 6 blocks per CU need <= 80 VGPRs.  The compiler lands at
+// 85 unasked and reaches 80 without scratch for the one-payload instance;
+// the two-payload instance would spill there, so it stays at 5 blocks.
+template <bool CARRY2>
+__global__ void __launch_bounds__(WFA_THREADS, CARRY2 ? 5 : 6)
+k_rs8_scatter_occ(const uint32_t* keys, const uint32_t* vals, int64_t n,
+                  int shift, const uint32_t* hist, int64_t nblocks,
+                  const uint32_t* dt, uint32_t* keys_out, uint32_t* vals_out,
+                  const uint32_t* vals2, uint32_t* vals2_out) {
+    static_assert(WFA_THREADS == 256, "one thread per digit");
+    static_assert(RS8_PER_BLOCK <= 65536, "staged position packs in 16 bits");
+    __shared__ uint32_t stage[RS8_PER_BLOCK];
+    // ranking: per-wave digit counters; afterwards: staged base of
+    // (wave, digit) = localBase[d] + counts of the waves before
+    __shared__ uint32_t cnt[WFA_THREADS / 64][256];
+    __shared__ uint32_t gd[256];  // global base - local base, per digit
+    __shared__ uint32_t wtot[2][WFA_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const uint64_t lt = ((uint64_t)1 << lane) - 1;
+    const int64_t blockStart = (int64_t)blockIdx.x * RS8_PER_BLOCK;
+    // everything below indexes the tile with 32-bit in-block positions:
+    // item j of this thread is tile item li0 + 64*j, valid below nblk_items
+    const int nblk_items = (int)min((int64_t)RS8_PER_BLOCK, n - blockStart);
+    const int li0 = wave * RS8_PER_WAVE + lane;
+    const uint32_t* kblk = keys + blockStart;
+    // thread `tid` owns digit `tid` in the scans
+    const uint32_t hbase = hist[(int64_t)tid * nblocks + blockIdx.x];
+    const uint32_t dtv = dt[tid];
+#pragma unroll
+    for (int w = 0; w < WFA_THREADS / 64; ++w) cnt[w][tid] = 0;
+    uint32_t mk[RS8_IPT];
+#pragma unroll
+    for (int j = 0; j < RS8_IPT; ++j) {
+        int li = li0 + j * 64;
+        mk[j] = (li < nblk_items) ? kblk[li] : 0;
+    }
+    __syncthreads();
+    // stable rank inside (wave, digit): counter before this round + lane
+    // rank in the round's same-digit ballot group
+    uint32_t mr[RS8_IPT];
+#pragma unroll
+    for (int j = 0; j < RS8_IPT; ++j) {
+        bool valid = li0 + j * 64 < nblk_items;
+        uint32_t d = (mk[j] >> shift) & 255;
+#ifdef RS8_OCC_MATCH_SELECT  // A/B: the LDS scatter's per-bit select form
+        uint64_t mask = __ballot(valid);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            uint64_t b = __ballot((d >> bit) & 1);
+            mask &= ((d >> bit) & 1) ? b : ~b;
+        }
+#else
+        // same group, fewer vector ops: collect the lanes that DIFFER from
+        // this lane in some digit bit (ballot XOR own bit, splat to 0 / ~0)
+        uint32_t dlo = 0, dhi = 0;
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            int32_t s = (int32_t)(d << (31 - bit)) >> 31;
+            uint64_t b = __ballot(s != 0);
+            dlo |= (uint32_t)b ^ (uint32_t)s;
+            dhi |= (uint32_t)(b >> 32) ^ (uint32_t)s;
+        }
+        uint64_t mask = __ballot(valid) & ~(((uint64_t)dhi << 32) | dlo);
+#endif
+        mr[j] = 0;
+        if (valid) {
+            uint32_t pre = cnt[wave][d];
+            mr[j] = pre + (uint32_t)__popcll(mask & lt);
+            if ((mask & lt) == 0) cnt[wave][d] = pre + (uint32_t)__popcll(mask);
+        }
+    }
+    __syncthreads();
+    {
+        uint32_t c0 = cnt[0][tid], c1 = cnt[1][tid], c2 = cnt[2][tid],
+                 c3 = cnt[3][tid];
+        uint32_t c = c0 + c1 + c2 + c3;
+        uint32_t ic = rs8_wave_incl_scan(c, lane);
+        uint32_t id = rs8_wave_incl_scan(dtv, lane);
+        if (lane == 63) {
+            wtot[0][wave] = ic;
+            wtot[1][wave] = id;
+        }
+        __syncthreads();
+        uint32_t oc = 0, od = 0;
+#pragma unroll
+        for (int w = 0; w < WFA_THREADS / 64 - 1; ++w)
+            if (w < wave) {
+                oc += wtot[0][w];
+                od += wtot[1][w];
+            }
+        uint32_t lb = ic - c + oc;     // staged base of digit `tid`
+        uint32_t db = id - dtv + od;   // global base of digit `tid`
+        cnt[0][tid] = lb;
+        cnt[1][tid] = lb + c0;
+        cnt[2][tid] = lb + c0 + c1;
+        cnt[3][tid] = lb + c0 + c1 + c2;
+        gd[tid] = hbase + db - lb;     // g = gd[d] + staged position (mod 2^32)
+    }
+    __syncthreads();
+    // round 1: keys.  mr[j] becomes the staged position of item j.
+#pragma unroll
+    for (int j = 0; j < RS8_IPT; ++j) {
+        if (li0 + j * 64 < nblk_items) {
+            uint32_t d = (mk[j] >> shift) & 255;
+            mr[j] += cnt[wave][d];
+            stage[mr[j]] = mk[j];
+        }
+    }
+    uint32_t mv[RS8_IPT];
+#pragma unroll
+    for (int j = 0; j < RS8_IPT; ++j) {
+        int li = li0 + j * 64;
+        // null vals = implicit iota: the payload is the global index
+        mv[j] = (li < nblk_items)
+                    ? (vals ? vals[blockStart + li] : (uint32_t)blockStart + (uint32_t)li)
+                    : 0;
+    }
+    __syncthreads();
+    // the digit of staged item tid + 256*j rides in bits 16..23 of mr[j]
+    // (above item j's own staged position) for the payload rounds
+#pragma unroll
+    for (int j = 0; j < RS8_IPT; ++j) {
+        int p = tid + j * WFA_THREADS;
+        if (p < nblk_items) {
+            uint32_t k = stage[p];
+            uint32_t d = (k >> shift) & 255;
+            keys_out[gd[d] + (uint32_t)p] = k;
+            mr[j] |= d << 16;
+        }
+    }
+    __syncthreads();
+    // round 2: payload
+#pragma unroll
+    for (int j = 0; j < RS8_IPT; ++j)
+        if (li0 + j * 64 < nblk_items) stage[mr[j] & 0xFFFF] = mv[j];
+    if (CARRY2) {
+#pragma unroll
+        for (int j = 0; j < RS8_IPT; ++j) {
+            int li = li0 + j * 64;
+            mv[j] = (li < nblk_items) ? vals2[blockStart + li] : 0;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < RS8_IPT; ++j) {
+        int p = tid + j * WFA_THREADS;
+        if (p < nblk_items) vals_out[gd[mr[j] >> 16] + (uint32_t)p] = stage[p];
+    }
+    if (CARRY2) {
+        // round 3: second payload
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RS8_IPT; ++j)
+            if (li0 + j * 64 < nblk_items) stage[mr[j] & 0xFFFF] = mv[j];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RS8_IPT; ++j) {
+            int p = tid + j * WFA_THREADS;
+            if (p < nblk_items) vals2_out[gd[mr[j] >> 16] + (uint32_t)p] = stage[p];
+        }
+    }
+}
+
+// WFA_RS8_SCATTER=lds selects the LDS scatter (k_rs8_scatter_lds with its
+// k_rs8_dbase launch) for the 8-bit path; anything else, or unset, the
+// low-LDS scatter.  Read once.
+static int wfa_rs8_env_lds() {
+    static int v = -1;
+    if (v < 0) {
+        const char* e = getenv("WFA_RS8_SCATTER");
+        v = (e && e[0] == 'l' && e[1] == 'd' && e[2] == 's' && e[3] == 0) ? 1 : 0;
+    }
+    return v;
+}
+
+// variant: 0 = as the environment says, 1 = low-LDS scatter, 2 = LDS scatter.
+// probe (may be null) is called after every kernel launch of the 8-bit path
+// with the kernel's short name and the pass number — the stage timer records
+// a hipEvent there.
 static void sort_pairs2_impl(wfa_stream_t s, uint32_t* slot, uint32_t* idx,
                              uint32_t* slot_tmp, uint32_t* idx_tmp,
                              uint32_t* val2, uint32_t* val2_tmp,
                              uint32_t* hist, int64_t n, int bits,
                              uint32_t** out_slot, uint32_t** out_idx,
                              uint32_t** out_val2, int implicit_iota,
-                             int base_shift, int skip_hist0) {
+                             int base_shift, int skip_hist0, int variant = 0,
+                             wfa_sort_probe_t probe = nullptr,
+                             void* probe_ctx = nullptr) {
     hipStream_t st = (hipStream_t)s;
     uint32_t *ka = slot, *va = idx, *kb = slot_tmp, *vb = idx_tmp;
     uint32_t *wa = val2, *wb = val2_tmp;
@@ -811,26 +1019,43 @@ static void sort_pairs2_impl(wfa_stream_t s, uint32_t* slot, uint32_t* idx,
         uint32_t* dt = hist + 256 * nb;
         uint32_t* dbase = dt + 256;
         int passes = (bits + 7) / 8;
+        const bool lds = variant ? variant == 2 : wfa_rs8_env_lds() != 0;
         for (int p = 0; p < passes; ++p) {
             int shift = base_shift + 8 * p;
             if (!(p == 0 && skip_hist0)) {
                 hipLaunchKernelGGL(k_rs8_hist, dim3(nb), dim3(WFA_THREADS), 0, st,
                                    ka, n, shift, hist, nb);
+                if (probe) probe(probe_ctx, "hist", p);
             }
             sdbg(st, "hist", p);
             hipLaunchKernelGGL(k_rs8_scan, dim3(256), dim3(256), 0, st, hist, nb, dt);
+            if (probe) probe(probe_ctx, "scan", p);
             sdbg(st, "scan", p);
-            hipLaunchKernelGGL(k_rs8_dbase, dim3(1), dim3(256), 0, st, dt, dbase);
-            sdbg(st, "dbase", p);
             uint32_t* va_eff = (first && implicit_iota) ? nullptr : va;
-            if (val2)
-                hipLaunchKernelGGL(k_rs8_scatter_lds<true>, dim3(nb),
-                                   dim3(WFA_THREADS), 0, st, ka, va_eff, n, shift,
-                                   hist, nb, dbase, kb, vb, wa, wb);
-            else
-                hipLaunchKernelGGL(k_rs8_scatter_lds<false>, dim3(nb),
-                                   dim3(WFA_THREADS), 0, st, ka, va_eff, n, shift,
-                                   hist, nb, dbase, kb, vb, wa, wb);
+            if (lds) {
+                hipLaunchKernelGGL(k_rs8_dbase, dim3(1), dim3(256), 0, st, dt, dbase);
+                if (probe) probe(probe_ctx, "dbase", p);
+                sdbg(st, "dbase", p);
+                if (val2)
+                    hipLaunchKernelGGL(k_rs8_scatter_lds<true>, dim3(nb),
+                                       dim3(WFA_THREADS), 0, st, ka, va_eff, n, shift,
+                                       hist, nb, dbase, kb, vb, wa, wb);
+                else
+                    hipLaunchKernelGGL(k_rs8_scatter_lds<false>, dim3(nb),
+                                       dim3(WFA_THREADS), 0, st, ka, va_eff, n, shift,
+                                       hist, nb, dbase, kb, vb, wa, wb);
+            } else {
+                // digit bases are scanned from dt inside the scatter
+                if (val2)
+                    hipLaunchKernelGGL(k_rs8_scatter_occ<true>, dim3(nb),
+                                       dim3(WFA_THREADS), 0, st, ka, va_eff, n, shift,
+                                       hist, nb, dt, kb, vb, wa, wb);
+                else
+                    hipLaunchKernelGGL(k_rs8_scatter_occ<false>, dim3(nb),
+                                       dim3(WFA_THREADS), 0, st, ka, va_eff, n, shift,
+                                       hist, nb, dt, kb, vb, wa, wb);
+            }
+            if (probe) probe(probe_ctx, "scatter", p);
             sdbg(st, "scatter", p);
             first = false;
             uint32_t* t;
@@ -890,6 +1115,22 @@ extern "C" void wfa_sort_pairs2_ph(wfa_stream_t s, uint32_t* slot, uint32_t* idx
     sort_pairs2_impl(s, slot, idx, slot_tmp, idx_tmp, val2, val2_tmp, hist, n,
                      bits, out_slot, out_idx, out_val2, implicit_iota,
                      base_shift, bits > 4 ? 1 : 0);
+}
+
+// wfa_sort_pairs2 / _ph with the scatter variant chosen per call and an
+// optional per-launch probe (tests and the stage timer)
+extern "C" void wfa_sort_pairs2_ex(wfa_stream_t s, uint32_t* slot, uint32_t* idx,
+                                   uint32_t* slot_tmp, uint32_t* idx_tmp,
+                                   uint32_t* val2, uint32_t* val2_tmp,
+                                   uint32_t* hist, int64_t n, int bits,
+                                   uint32_t** out_slot, uint32_t** out_idx,
+                                   uint32_t** out_val2, int implicit_iota,
+                                   int base_shift, int skip_hist0, int variant,
+                                   wfa_sort_probe_t probe, void* probe_ctx) {
+    sort_pairs2_impl(s, slot, idx, slot_tmp, idx_tmp, val2, val2_tmp, hist, n,
+                     bits, out_slot, out_idx, out_val2, implicit_iota,
+                     base_shift, (skip_hist0 && bits > 4) ? 1 : 0, variant, probe,
+                     probe_ctx);
 }
 
 extern "C" void wfa_sort_pairs(wfa_stream_t s, uint32_t* slot, uint32_t* idx,

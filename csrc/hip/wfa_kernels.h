@@ -91,6 +91,19 @@ void wfa_sort_pairs2_ph(wfa_stream_t s, uint32_t* slot, uint32_t* idx,
                         int64_t n, int bits, uint32_t** out_slot,
                         uint32_t** out_idx, uint32_t** out_val2,
                         int implicit_iota, int base_shift);
+// the same sort with the 8-bit scatter variant chosen per call (0 = as
+// WFA_RS8_SCATTER says, 1 = low-LDS scatter, 2 = LDS scatter), the pass-0
+// histogram optionally precomputed (skip_hist0), and an optional probe called
+// after every kernel launch of the 8-bit path with the kernel's short name
+// ("hist", "scan", "dbase", "scatter") and the pass number
+typedef void (*wfa_sort_probe_t)(void* ctx, const char* kernel, int pass);
+void wfa_sort_pairs2_ex(wfa_stream_t s, uint32_t* slot, uint32_t* idx,
+                        uint32_t* slot_tmp, uint32_t* idx_tmp,
+                        uint32_t* val2, uint32_t* val2_tmp, uint32_t* hist,
+                        int64_t n, int bits, uint32_t** out_slot,
+                        uint32_t** out_idx, uint32_t** out_val2,
+                        int implicit_iota, int base_shift, int skip_hist0,
+                        int variant, wfa_sort_probe_t probe, void* probe_ctx);
 int64_t wfa_sort_nblocks(int64_t n);
 int64_t wfa_sort_hist_u32(int64_t cap);  // hist scratch size in u32
 
